@@ -20,6 +20,12 @@ stream around that launch). traffic = HBM bytes per launch of that kernel from t
 (profiles/pmc_traffic.json: FETCH_SIZE doubled per the gfx950 note of the MI355X guide, plus WRITE_SIZE).
 CPU baseline: the oracle (C++ restatement of the reference engine, one core) on a bounded sample of the same
 workload.
+
+A plain run (no --full) sets up, warms up, times the steps and prints the result line: the headline value, ms_per_step
+and the roofline figures that come from the timed steps' own kernel timings. --full adds the legs that take runs of
+their own: the ordered steps, the CPU baselines, the ordered result gather, the end-to-end (host push -> poll) steps
+and the oracle parity check (each can still be switched off with its --no-* option). --dump-outputs DIR writes the
+match records of the last timed step (see dump_matches).
 """
 import argparse
 import ctypes
@@ -44,6 +50,33 @@ T_START = time.time()
 def log(msg):
     """progress on stderr (the JSON line is the only stdout output)"""
     print("[bench %6.1fs] %s" % (time.time() - T_START, msg), file=sys.stderr, flush=True)
+
+
+DUMP_ROWS = 2_000_000  # rows of the --dump-outputs sample (3 float64 columns: 48 MB)
+DUMP_SEED = 20240607
+TS_POOL_FRAC = 0.5  # share of the free device memory that the steps' timestamp columns may take (0.8 GB per step)
+
+
+def dump_matches(path_dir, rank, world, ts, e1, e2):
+    """--dump-outputs: the match records of the last timed step (device tensors ts, e1id, e2id, in delivery order: the
+    engine's storage order depends on the order in which workgroups append) as float64 .npy files (every value is an
+    integer below 2^53). matches.npy: [rows, 3] = (ts, e1id, e2id), every record if there are at most DUMP_ROWS, else
+    the records at DUMP_ROWS seeded positions of the delivery order (the same positions for the same record count).
+    summary.npy: [record count, sum(ts), sum(e1id), sum(e2id)], the sums over ALL records modulo 2^32."""
+    import torch
+    total = int(ts.numel())
+    if total > DUMP_ROWS:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_ROWS))
+        idx = torch.from_numpy(pos).to(ts.device)
+        rows = torch.stack([ts[idx], e1[idx], e2[idx]], dim=1)
+    else:
+        rows = torch.stack([ts, e1, e2], dim=1)
+    sums = [float(int((c & 0xffffffff).sum().item()) % (1 << 32)) for c in (ts, e1, e2)]
+    os.makedirs(path_dir, exist_ok=True)
+    sfx = "" if world == 1 else ".rank%d" % rank
+    np.save(os.path.join(path_dir, "matches%s.npy" % sfx), rows.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path_dir, "summary%s.npy" % sfx), np.array([float(total)] + sums, dtype=np.float64))
+    log("wrote %d of %d match records to %s" % (rows.shape[0], total, path_dir))
 
 
 def gen_shard(n, keys, rank, world, seed=7):
@@ -472,7 +505,10 @@ def run_c5(args, rank, world, local, dist):
         ent = json.load(open(tpath)).get("c5", {}).get(names.get(dom, dom).split(" ")[0])
         if ent and ent.get("events_per_launch") == args.c5_batch:
             out["roofline"]["traffic"] = ent["fetch_bytes"] + ent["write_bytes"]
-    if rank == 0 and last_merged[0] is not None:  # the last step's merged records are in delivery order
+    if args.dump_outputs:  # the last step's records as its caller has them: merged on rank 0, in delivery order
+        if rank == 0:
+            dump_matches(args.dump_outputs, 0, 1, last_merged[0]["ts"], last_merged[0]["e1"], last_merged[0]["e2"])
+    if args.full and rank == 0 and last_merged[0] is not None:  # the last step's merged records are in delivery order
         e2, e1 = last_merged[0]["e2"], last_merged[0]["e1"]
         ok = bool(((e2[1:] > e2[:-1]) | ((e2[1:] == e2[:-1]) & (e1[1:] > e1[:-1]))).all().item()) \
             if e2.numel() > 1 else True
@@ -576,6 +612,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--events", type=int, default=100_000_000, help="events per GPU per step")
     ap.add_argument("--keys", type=int, default=10_000, help="keys per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: ordered steps, CPU baselines, ordered result "
+                         "gather, end-to-end steps, oracle parity (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match records of the last timed step to DIR/matches.npy and DIR/summary.npy")
     ap.add_argument("--cpu-sample", type=int, default=3_000_000)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--parity-sample", type=int, default=3_000_000,
@@ -592,6 +633,15 @@ def main():
     ap.add_argument("--c5-shard", default=None,
                     help="C5 on one process: run shard R/W (rank R of a W-GPU run) instead of this process's rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_cpu = args.no_parity = args.no_ordered = True
+        args.e2e_steps = 0
+        if args.config == "c2":  # (C5's gather is part of its step: --no-gather stays the caller's choice there)
+            args.no_gather = True
+    if args.config == "c5" and args.dump_outputs and args.no_gather:
+        raise SystemExit("bench.py: C5's --dump-outputs writes the gathered records: not with --no-gather")
 
     # --gpus N is honoured: without a launcher (no WORLD_SIZE in the environment) this process starts the N ranks
     # itself -- torch.distributed.run as a CHILD process, before anything here touches the GPU -- and exits with its
@@ -652,42 +702,76 @@ def main():
     d_ts0 = torch.from_numpy(cols["ts"]).to(dev)
     span = int(cols["ts"][-1] - cols["ts"][0]) + 1
     nsteps = args.warmup + args.steps
-    ts_steps = [d_ts0 + s * span for s in range(nsteps)]  # consecutive batches of one stream (the ordered steps and
-                                                          # the gather leg continue its time after them)
-    torch.cuda.synchronize()
+    # consecutive batches of one stream: step s carries the timestamps d_ts0 + s * span (the ordered steps and the
+    # gather leg continue its time after the timed steps). The columns are made before the clock starts: all of them
+    # if they fit in TS_POOL_FRAC of the free device memory, else that many steps at a time, and the clock stops while
+    # the pool is refilled (device memory does not grow with --steps).
+    free_b = torch.cuda.mem_get_info(dev)[0]
+    ts_pool = [torch.empty_like(d_ts0) for _ in range(max(1, min(nsteps, int(free_b * TS_POOL_FRAC) // (8 * n))))]
 
-    def step(s):
-        rt.push_device("StockStream", n, ts_steps[s].data_ptr(),
+    held = [0, 0]  # the pool holds the columns of steps held[0] .. held[1] - 1
+
+    def timed(first, count, fn, ahead=0):
+        """fn(ts column of step s) for s = first .. first + count - 1; returns the seconds inside the steps. ahead:
+        steps after these whose columns are made with them, if the pool has room"""
+        total, s = 0.0, first
+        while s < first + count:
+            if not held[0] <= s < held[1]:
+                held[0], held[1] = s, s + min(len(ts_pool), first + count + ahead - s)
+                for j in range(held[1] - held[0]):
+                    torch.add(d_ts0, (s + j) * span, out=ts_pool[j])
+            c = min(held[1], first + count) - s
+            if dist is not None:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for j in range(s - held[0], s - held[0] + c):
+                fn(ts_pool[j])
+            torch.cuda.synchronize()
+            if dist is not None:
+                dist.barrier()
+            total += time.perf_counter() - t0
+            s += c
+        return total
+
+    keys_k = ["ms_kg_hist", "ms_kg_prefix", "ms_kg_scatter", "ms_chain_carry", "ms_chain_match"]
+    acc = {k: 0.0 for k in keys_k}
+    done = {"steps": 0, "matches": 0, "st": None}
+
+    def step(d_ts):
+        rt.push_device("StockStream", n, d_ts.data_ptr(),
                        [d_id.data_ptr(), d_sym.data_ptr(), d_price.data_ptr(), d_vol.data_ptr()])
         rt.flush(deliver=False)
-        rt.discard()  # matches stay in HBM (device-resident measurement)
+        done["steps"] += 1
+        if not (args.dump_outputs and done["steps"] == nsteps):  # (the last step's records wait for the dump, which
+            rt.discard()  # exports them after the clock stops) matches stay in HBM (device-resident measurement)
         st = rt.stats()
         if dist is not None:  # batch-boundary match-count all-gather (global output offsets)
             cnt = torch.tensor([st.matches], dtype=torch.int64, device=dev)
             allc = [torch.empty_like(cnt) for _ in range(world)]
             dist.all_gather(allc, cnt)
-        return st
+        if done["steps"] > args.warmup:
+            done["matches"] += st.matches
+            for k in keys_k:
+                acc[k] += getattr(st, k)
+        done["st"] = st
 
     log("warm-up (%d steps)" % args.warmup)
-    for s in range(args.warmup):
-        step(s)
+    timed(0, args.warmup, step, ahead=args.steps)
     log("timed steps (%d)" % args.steps)
-    keys_k = ["ms_kg_hist", "ms_kg_prefix", "ms_kg_scatter", "ms_chain_carry", "ms_chain_match"]
-    acc = {k: 0.0 for k in keys_k}
-    matches = 0
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s in range(args.warmup, nsteps):
-        st = step(s)
-        matches += st.matches
-        for k in keys_k:
-            acc[k] += getattr(st, k)
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = timed(args.warmup, args.steps, step)
+    matches, st = done["matches"], done["st"]
+    if args.dump_outputs:  # the last timed step's records, in delivery order (sdg_export_ordered)
+        cap = n + n // 4 + 4096
+        x_ts = torch.empty(cap, dtype=torch.int64, device=dev)
+        x_seq = torch.empty(cap, dtype=torch.int64, device=dev)
+        x_vals = torch.empty((2, cap), dtype=torch.int64, device=dev)
+        cnt = rt.export_ordered(0, cap, x_ts.data_ptr(), x_seq.data_ptr(), 0, x_vals.data_ptr())
+        if cnt != st.matches:
+            raise RuntimeError("--dump-outputs: exported %d records, the last step matched %d" % (cnt, st.matches))
+        dump_matches(args.dump_outputs, rank, world, x_ts[:cnt], x_vals[0, :cnt], x_vals[1, :cnt])
+        del x_ts, x_seq, x_vals
+        torch.cuda.empty_cache()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -750,25 +834,19 @@ def main():
         o_ts = torch.empty(cap, dtype=torch.int64, device=dev)
         o_seq = torch.empty(cap, dtype=torch.int64, device=dev)
         o_vals = torch.empty((2, cap), dtype=torch.int64, device=dev)
-        ots = [d_ts0 + (nsteps + 2 + s) * span for s in range(K + 1)]  # (the stream's time continues)
+        onum = [0]
 
-        def ostep(s):
-            rt.push_device("StockStream", n, ots[s].data_ptr(),
+        def ostep(d_ts):
+            rt.push_device("StockStream", n, d_ts.data_ptr(),
                            [d_id.data_ptr(), d_sym.data_ptr(), d_price.data_ptr(), d_vol.data_ptr()])
             rt.flush(deliver=False)
-            return rt.export_ordered(0, cap, o_ts.data_ptr(), o_seq.data_ptr(), 0, o_vals.data_ptr())
-        ostep(0)  # (warm-up: the ordering pass sizes its workspaces on first use)
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        orecs = 0
-        for s in range(1, K + 1):
-            orecs += ostep(s)
-        torch.cuda.synchronize()
-        if dist is not None:
-            dist.barrier()
-        oel = time.perf_counter() - t0
+            onum[0] += rt.export_ordered(0, cap, o_ts.data_ptr(), o_seq.data_ptr(), 0, o_vals.data_ptr())
+        # (the stream's time continues at step nsteps + 2; the first is a warm-up: the ordering pass sizes its
+        # workspaces on first use)
+        timed(nsteps + 2, 1, ostep, ahead=K)
+        onum[0] = 0
+        oel = timed(nsteps + 3, K, ostep)
+        orecs = onum[0]
         if dist is not None:
             t = torch.tensor([oel], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
