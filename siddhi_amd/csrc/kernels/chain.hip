@@ -16,6 +16,7 @@
 
 #include <limits>
 #include <stdexcept>
+#include <type_traits>
 
 #include "../engine/eval.h"
 #include "kernels.h"
@@ -877,11 +878,11 @@ __global__ __launch_bounds__(256, 8) void chain_carry_wave_k(const ChainArgs* __
 // form one run in s_ts / s_x in arrival order -- the key-sorted view of chain_match_k, built per block in LDS
 // instead of by a second radix pass over HBM.
 // soft bounds checks (debugging aid): a failed check sets bit `id` of flags[2] and the access is skipped
-#define FU_OK(cond, id) ((cond) ? true : (atomicOr(&a.flags[2], 1 << (id)), false))
+#define FU_OK(cond, id) ((cond) ? true : (atomicOr(&h.flags[2], 1 << (id)), false))
 // SDG_DEBUG progress trace: the last stage each wave reached, readable by the host after a fault
 #define FU_TRACE(stage)                                                                                     \
     do {                                                                                                    \
-        if (a.dbg && lane == 0) a.dbg[(int64_t)blockIdx.x * 4 + w] = (stage);                              \
+        if (h.dbg && lane == 0) h.dbg[(int64_t)blockIdx.x * 4 + w] = (stage);                              \
     } while (0)
 
 static_assert(FU_THREADS >= 256, "chain_fused_k: one thread per local key in the run tables");
@@ -924,17 +925,36 @@ static_assert(FU_ROWS < 65536, "chain_fused_k: u16 rows / run offsets");
 // the partial's y iff x SOP y, with the host folding e2's side into SOP. Only the work-queue match pass is compiled
 // then (the deque / fixed-scan A/B paths and the run-time operator dispatch drop out: fewer SGPRs, no uniform
 // branches in the scan loop)
+// Arguments (round 7): the SOP build takes FusedArgs by value (kernels.h) -- `h`, what the block start, the staging
+// and the matching read, is then the kernel-argument segment (SGPRs, global_* accesses); the other builds read
+// everything through `pa` as before (h = *pa) and get an unused int. The SOP build keeps `pa` for the emission (through
+// fu_gp), the carries and its rare paths.
+template <bool FIX>
+__device__ __forceinline__ const auto& fu_hot(const std::conditional_t<FIX, FusedArgs, int>& fa, const ChainArgs& a) {
+    if constexpr (FIX) return fa;
+    else return a;
+}
+// a pointer read out of the ChainArgs copy as a pointer to global memory (G; every buffer of a flush is device memory),
+// or as it is
+template <bool G, class P>
+__device__ __forceinline__ auto fu_gp(P* p) {
+    if constexpr (G) return (__attribute__((address_space(1))) P*)p;
+    else return p;
+}
 template <int K, bool SAME, int W, bool ONEK = false, bool OC = false, int SOP = -1>
-__global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* __restrict__ pa) {
+__global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* __restrict__ pa,
+                                                               const std::conditional_t<SOP >= 0, FusedArgs, int> fa) {
     using C = KT<K>;
     using T = typename C::T;
     constexpr bool FIX = SOP >= 0;
+    constexpr bool FIXS = FIX && SDG_FIX_STAGE;  // the SOP build's staging: slim view, the scan column's own width
     static_assert(!FIX || SOP == CMP_GT || SOP == CMP_GE || SOP == CMP_LT || SOP == CMP_LE, "SOP: an ordering operator");
     static_assert(!FIX || (SAME && !ONEK && !OC), "SOP: the many-key build of the scan's own kind");
     constexpr int NW = FU_THREADS / 64;
     constexpr int WROWS = FU_ROWS / NW;  // staged rows ranked by one wave (contiguous)
     const ChainArgs& a = *pa;
     const ChainSpec& sp = a.sp;
+    const auto& h = fu_hot<FIX>(fa, a);
     __shared__ uint32_t s_ts[FU_ROWS];   // ts - ts of the block's first staged row (bucket rows are time-ordered)
     __shared__ int64_t s_x[FU_ROWS];
     __shared__ uint16_t s_row[FU_ROWS];
@@ -950,7 +970,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     // XCD-aware block order (kernels.h xcd_block): virtual id v gives each XCD a contiguous run of segments, so
     // neighbouring segments (which share halo rows) hit one L2
-    const uint32_t v = xcd_block(blockIdx.x, gridDim.x, (uint32_t)a.xcds);
+    const uint32_t v = xcd_block(blockIdx.x, gridDim.x, (uint32_t)h.xcds);
     if (t == 0) sb[0] = -1;
     __syncthreads();
     const uint32_t tS = (OC && a.tm) ? a.tm[0] : 0u;
@@ -985,51 +1005,94 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
             sb[0] = t;
             sb[1] = (int)ss;
         }
-    } else if (t < a.nb && a.bseg[t] <= v && v < a.bseg[t + 1]) {
-        sb[0] = t;
-        sb[1] = (int)(v - a.bseg[t]);
+    } else if (t < h.nb) {
+        // both loads in flight: `&&` (and a plain `if` on both, which the compiler turns back into it) loads
+        // bseg[t + 1] only after bseg[t] has arrived and passed
+        const uint32_t s0 = h.bseg[t], s1 = h.bseg[t + 1];
+        if ((uint32_t)(v - s0) < (uint32_t)(s1 - s0)) {  // s0 <= v < s1 (s0 <= s1: a prefix sum)
+            sb[0] = t;
+            sb[1] = (int)(v - s0);
+        }
     }
     __syncthreads();
-    const int b = sb[0];
+    // (block-uniform, but read from LDS: the SOP build says so, and its bucket range is three scalar loads)
+    const int b = FIX ? __builtin_amdgcn_readfirstlane(sb[0]) : sb[0];
     FU_TRACE(1);
     if (b < 0) { FU_TRACE(99); return; }  // block-uniform: past the plan
-    const int64_t be = a.bstart[b + 1];
+    const int seg = FIX ? __builtin_amdgcn_readfirstlane(sb[1]) : sb[1];
+    const int64_t be = h.bstart[b + 1];
     const int fown = ONEK ? a.fu_own : FU_OWN;
-    const int64_t lo = (int64_t)a.bstart[b] + (int64_t)sb[1] * fown;
-    const int64_t oe = a.bown ? (int64_t)a.bown[b] : be;  // the bucket's own rows end (sub-batches: its halo after)
+    const int64_t lo = (int64_t)h.bstart[b] + (int64_t)seg * fown;
+    const int64_t oe = h.bown ? (int64_t)h.bown[b] : be;  // the bucket's own rows end (sub-batches: its halo after)
     const int own = (int)min((int64_t)fown, oe - lo);
     const int nr = (int)min((int64_t)FU_ROWS, be - lo);
     const bool to_end = lo + nr == be;  // the staged rows reach the bucket's (= batch's) end for every key
-    const int col = sp.scan_col;
-    const uint8_t kind = sp.scan_col_kind;
-    const int nl = 1 << a.lbits;
+    const int col = FIXS ? 0 : sp.scan_col;  // (the SOP build: its column is h.xcol, of kind K = its own, SAME)
+    const uint8_t kind = FIXS ? (uint8_t)K : sp.scan_col_kind;
+    const int nl = 1 << h.lbits;
     // ---- stage: coalesced loads (all rounds in flight), stable rank by local key -----------------------------
     for (int d = t; d < 256; d += FU_THREADS)
 #pragma unroll
         for (int x = 0; x < NW; ++x) wc[x][d] = 0;
-    if (!FU_OK(lo >= 0 && nr >= 1 && lo + nr <= a.n && b < a.nb, 1)) return;
-    const int64_t tbase = vts(a, lo);
-    const int64_t tlast = vts(a, lo + nr - 1);
+    if (!FU_OK(lo >= 0 && nr >= 1 && lo + nr <= h.n && b < h.nb, 1)) return;
     uint32_t rkey[FU_PT];
-    int64_t rts[FU_PT], rx[FU_PT];
-    const void* xcol = a.cols[col];
+    int64_t rx[FU_PT];
+    // the staged ts as u32 offsets from the block's first row (tbase). The SOP build never widens them: the view's
+    // ts32 are offsets from one base already, so the difference of two of them is the offset (mod 2^32, exact: the
+    // batch's rows lie within 2^32 ms), and only tbase itself -- for out_ts and the carry records -- is 64-bit
+    uint32_t roff[FU_PT];
+    int64_t rts[FIXS ? 1 : FU_PT];
+    int64_t tbase, tlast;
+    uint32_t tl_off;  // the last staged row's offset
+    if constexpr (FIXS) {
+        // one trip: the block's first and last ts and every row load are issued before anything waits on them
+        // (scalar bases at the block's first row, so a lane's offset is its row in the block: < FU_ROWS, 32-bit)
+        const uint8_t* const lkp = h.lkey + lo;
+        const uint32_t* const tsp = h.ts32 + lo;
+        const int64_t* const xp8 = (const int64_t*)h.xcol + lo;
+        const int32_t* const xp4 = (const int32_t*)h.xcol + lo;
+        const uint32_t t_lo = tsp[0], t_hi = tsp[(uint32_t)(nr - 1)];
+        uint32_t rt32[FU_PT];
+        uint8_t rlk[FU_PT];
 #pragma unroll
-    for (int r = 0; r < FU_PT; ++r) {
-        const int row = w * WROWS + r * 64 + lane;
-        const int64_t g = lo + min(row, nr - 1);  // clamped: rows past nr are loaded but not staged
-        if ((FIX && SDG_FIX_STAGE) || a.lkey) {  // slim view: u8 local key, u32 ts offset (the SOP build: always)
-            rkey[r] = (uint32_t)a.lkey[g] << a.bbits;
-            rts[r] = tbase + (int64_t)(uint32_t)(a.ts32[g] - a.ts32[lo]);
-        } else {
-            rkey[r] = ONEK ? 0u : a.key[g];
-            rts[r] = a.ts[g];
+        for (int r = 0; r < FU_PT; ++r) {
+            const uint32_t row = (uint32_t)(w * WROWS + r * 64 + lane);
+            const uint32_t g = min(row, (uint32_t)(nr - 1));  // clamped: rows past nr are loaded but not staged
+            rlk[r] = lkp[g];
+            rt32[r] = tsp[g];
+            // the scan column's own kind (SAME): its width, no kind dispatch
+            rx[r] = sizeof(T) == 8 ? xp8[g] : (int64_t)xp4[g];
         }
-        if constexpr (FIX && SDG_FIX_STAGE)  // the scan column's own kind (SAME): its width, no kind dispatch
-            rx[r] = sizeof(T) == 8 ? ((const int64_t*)xcol)[g] : (int64_t)((const int32_t*)xcol)[g];
-        else
+#pragma unroll
+        for (int r = 0; r < FU_PT; ++r) {
+            rkey[r] = (uint32_t)rlk[r];  // (the local key itself: the ranking below does not shift it)
+            roff[r] = rt32[r] - t_lo;
+        }
+        tbase = *h.ts_base + (int64_t)t_lo;
+        tl_off = t_hi - t_lo;
+        tlast = tbase + (int64_t)tl_off;
+        rts[0] = 0;
+    } else {
+        tbase = vts(a, lo);
+        tlast = vts(a, lo + nr - 1);
+        tl_off = (uint32_t)(tlast - tbase);
+        const void* xcol = a.cols[col];
+#pragma unroll
+        for (int r = 0; r < FU_PT; ++r) {
+            const int row = w * WROWS + r * 64 + lane;
+            const int64_t g = lo + min(row, nr - 1);  // clamped: rows past nr are loaded but not staged
+            if (a.lkey) {  // slim view: u8 local key, u32 ts offset
+                rkey[r] = (uint32_t)a.lkey[g] << a.bbits;
+                rts[r] = tbase + (int64_t)(uint32_t)(a.ts32[g] - a.ts32[lo]);
+            } else {
+                rkey[r] = ONEK ? 0u : a.key[g];
+                rts[r] = a.ts[g];
+            }
             rx[r] = kind == VK_F64 || kind == VK_I64 ? ((const int64_t*)xcol)[g] : load_col(xcol, kind, g);
+            roff[r] = (uint32_t)(rts[r] - tbase);
+        }
     }
-    if (ONEK) {  // one-key batch: arrival order must be time order (the chain path's precondition)
+    if constexpr (ONEK) {  // one-key batch: arrival order must be time order (the chain path's precondition)
         bool bad = false;
 #pragma unroll
         for (int r = 0; r < FU_PT; ++r) {
@@ -1041,12 +1104,15 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         if (__ballot(bad) && lane == 0) atomicOr(&a.flags[3], 1);
     }
     FU_TRACE(2);
-    if (!(FIX && SDG_FIX_STAGE) && tlast - tbase > (int64_t)0xFFFFFFFF) {  // staged span does not fit the u32 offsets (slim view:
+    if (!FIXS && tlast - tbase > (int64_t)0xFFFFFFFF) {  // staged span does not fit the u32 offsets (slim view:
         if (t == 0) atomicOr(&a.flags[3], 1);     // it does) -> the host reruns the batch on the radix path
         return;                                   // block-uniform
     }
-    if (a.fu_skip & 4) {
-        if (rts[0] == -12345 && rx[FU_PT - 1] == 7 && rkey[FU_PT / 2] == 9) a.flags[2] = 1;  // keep the loads alive
+    if (h.fu_skip & 4) {
+        bool never = tl_off == 0xFFFFFFF3u;  // keep every load alive
+#pragma unroll
+        for (int r = 0; r < FU_PT; ++r) never = never && roff[r] == 0xFFFFFFF1u && rx[r] == 7 && rkey[r] == 9;
+        if (never) h.flags[2] = 1;
         return;
     }
     __syncthreads();
@@ -1058,9 +1124,10 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
     for (int r = 0; r < FU_PT; ++r) {
         const int row = w * WROWS + r * 64 + lane;
         const bool valid = row < nr;
-        const uint32_t d = valid ? (rkey[r] >> a.bbits) & (uint32_t)(nl - 1) : 0u;  // mask: no-op for keys < K
+        const uint32_t lk = FIXS ? rkey[r] : rkey[r] >> h.bbits;
+        const uint32_t d = valid ? lk & (uint32_t)(nl - 1) : 0u;  // mask: no-op for keys < K
         uint64_t peers = __ballot(valid);
-        for (int bit = 0; bit < a.lbits; ++bit) {
+        for (int bit = 0; bit < h.lbits; ++bit) {
             const bool on = (d >> bit) & 1u;
             const uint64_t m = __ballot(on);
             peers &= on ? m : ~m;
@@ -1095,7 +1162,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         if (row < nr) {
             const uint32_t pos = lstart[dig[r]] + wc[w][dig[r]] + rank[r];
             if (!FU_OK(pos < (uint32_t)nr, 2)) continue;
-            s_ts[sw(pos)] = (uint32_t)(rts[r] - tbase);
+            s_ts[sw(pos)] = roff[r];
             s_x[sw(pos)] = rx[r];
             s_row[sw(pos)] = (uint16_t)row;
             s_lk[sw(pos)] = dig[r];
@@ -1104,12 +1171,14 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
     }
     __syncthreads();
     FU_TRACE(4);
-    if (a.fu_skip & 8) return;
+    if (h.fu_skip & 8) return;
     // ---- match: position pos = k * FU_THREADS + t (a run of consecutive positions per round) ---------------
+    // (the SOP build: the operator is compiled in and the e1 filter's shape comes with FusedArgs -- nothing of the
+    // spec is read here)
     const bool stream_e1 = FIX || sp.scan_mode == SCAN_E1;
     const bool e1_is_x = FIX || (stream_e1 && sp.e1_col == col && sp.e1_col_kind == kind);
-    const CmpMask m = cmp_mask(sp.scan_mode == SCAN_TRUE ? OP_ALWAYS : sp.scan_op);
-    const bool left = sp.scan_e2_left;
+    const CmpMask m = FIX ? CmpMask{} : cmp_mask(sp.scan_mode == SCAN_TRUE ? OP_ALWAYS : sp.scan_op);
+    const bool left = FIX ? true : (bool)sp.scan_e2_left;
     // x (a later row's value) completes the partial whose e1 operand is y
     auto beats = [&](T x, T y) -> bool {
         if constexpr (SOP == CMP_GT) return x > y;
@@ -1119,31 +1188,46 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         else return left ? cmp_m(m, x, y) : cmp_m(m, y, x);
     };
     // bucket rows are time-ordered (bucketize checked it), so a later row's offset is never below the start's
-    const uint64_t within_u = sp.has_within ? (uint64_t)sp.within_ms : ~0ull;
-    const FastPred& f0 = sp.f0;
-    const bool f0_on_x = a.f0_on_x;
-    const bool f0_typed = f0_on_x && SAME && f0.t == K;  // c0 = `x OP const` in the scan's own type
-    const CmpMask m0 = cmp_mask(f0.op);
-    const T k0 = C::get(f0.konst);
-    const T kc = C::get(sp.scan_konst);
+    uint64_t within_u;
+    bool f0_on_x, f0_typed, f0_true = false;  // f0_typed: c0 = `x OP const` in the scan's own type
+    CmpMask m0;
+    T k0, kc;
+    if constexpr (FIX) {
+        within_u = fa.within_u;
+        f0_on_x = false;  // (FU_F0_GEN: read below, on that path only)
+        f0_typed = fa.f0_mode == FU_F0_TYPED;
+        f0_true = fa.f0_mode == FU_F0_TRUE;
+        m0 = cmp_mask((uint8_t)fa.f0_op);
+        k0 = C::get(fa.f0_konst);
+        kc = T(0);  // (every partial's operand is its e1 value)
+    } else {
+        within_u = sp.has_within ? (uint64_t)sp.within_ms : ~0ull;
+        f0_on_x = a.f0_on_x;
+        f0_typed = f0_on_x && SAME && sp.f0.t == K;
+        m0 = cmp_mask(sp.f0.op);
+        k0 = C::get(sp.f0.konst);
+        kc = C::get(sp.scan_konst);
+    }
     // a partial still pending when its key's staged rows end: carried at the flush's end, dead at a sub-batch's (its
     // halo reaches past the window), else its key continues past the staged rows (the HBM scan)
-    const uint16_t ran_off = to_end ? (a.sub_dead ? R_NONE : R_CARRY) : R_OVF;
+    const uint16_t ran_off = to_end ? (h.sub_dead ? R_NONE : R_CARRY) : R_OVF;
     // ... unless the staged span already reaches past its window: every later row of the bucket (so every later
-    // event of its key) has ts >= tlast, where the partial is expired (isExpired) -- dead, no HBM scan needed
-    const uint32_t tl_off = (uint32_t)(tlast - tbase);
+    // event of its key) has ts >= tlast (offset tl_off), where the partial is expired (isExpired) -- dead, no HBM
+    // scan needed
     auto ran_res = [&](int pos) -> uint16_t {
         return (!to_end && (uint64_t)(tl_off - s_ts[sw(pos)]) > within_u) ? R_NONE : ran_off;
     };
     auto c0_at = [&](int pos, int64_t xr, T xv) -> bool {  // the e1 filter of the row at `pos`
         if (f0_typed) return cmp_m(m0, xv, k0);
-        if (f0_on_x) return cmp(f0.op, f0.t, cvt(xr, kind, f0.t), f0.konst);
+        if (FIX && f0_true) return true;
+        const FastPred& f0 = sp.f0;
+        if (FIX ? (bool)a.f0_on_x : f0_on_x) return cmp(f0.op, f0.t, cvt(xr, kind, f0.t), f0.konst);
         ChainAcc acc{&a, View{}, lo + s_row[sw(pos)], -1, -1};
         return f0.kind == FP_TRUE ? true : fast_pass(f0, acc);
     };
-    if (a.fu_skip & 16) {
+    if (h.fu_skip & 16) {
         // phase timing: no matching
-    } else if (!(a.fu_skip & 256)) {
+    } else if (!(h.fu_skip & 256)) {
         // ---- wave work queue (round 5): each candidate's result is independent of every other partial's (DESIGN.md
         // 4: a partial completes at the first later row of its key that passes c1 while it is alive), so it is a
         // forward scan over its key's run in LDS. Scan lengths are uneven (a high e1 price waits for expiry, ~a window
@@ -1530,7 +1614,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         const uint32_t run = __shfl(inc, 63);
         if (lane == 0) {
             unsigned long long* ctr = ci == 0 ? a.out_count : ci == 1 ? a.carry_count : a.ovf_count;
-            if (a.fu_skip & 32) bbase[ci] = ci == 0 ? (unsigned long long)v * fown : 0ull;  // phase timing only
+            if (h.fu_skip & 32) bbase[ci] = ci == 0 ? (unsigned long long)v * fown : 0ull;  // phase timing only
             else bbase[ci] = run ? atomicAdd(ctr, (unsigned long long)run) : 0ull;
         }
     }
@@ -1538,7 +1622,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
     // ---- emit matches: slots and rows of every round first (LDS only), then every load of every round, then
     // the stores. Loads are issued before any store: gfx9's vmcnt retires loads and stores in issue order, so a
     // load issued after a store would wait for that store too. --------------------------------------------------
-    if (a.fu_skip & 2) return;
+    if (h.fu_skip & 2) return;
     constexpr uint32_t NOSLOT = 0xFFFFFFFFu;
     uint32_t slot[FU_PT], prow[FU_PT], qrow[FU_PT];
     bool any_co = false;  // this lane has carries / overflow rows
@@ -1553,7 +1637,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         if (out < MQ_OVF) {
             const uint64_t sl = bbase[0] + wcnt[0][k][w] + (uint32_t)__popcll(bm & lt);
             if (sl >= (uint64_t)a.out_cap) {
-                atomicOr(&a.flags[0], 1);
+                atomicOr(&h.flags[0], 1);
             } else {
                 slot[k] = (uint32_t)sl;
                 prow[k] = s_row[sw(pos)];
@@ -1571,39 +1655,49 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         return (in.c == 0 || in.c == -1) && in.a < 2 && (in.k == VK_I64 || in.k == VK_F64) && !a.nulls[in.b];
     };
     const bool fast = n_out <= 2 && (n_out < 1 || plain8(in0)) && (n_out < 2 || plain8(in1));
+    const bool e2_0 = in0.a != 0, e2_1 = in1.a != 0;  // output 0 / 1 reads e2's row
     const int jfrom = fast ? n_out : 0;  // output columns left to the general loop below
     {
-        const int64_t* c0p = n_out >= 1 ? (const int64_t*)a.cols[in0.b] : nullptr;
-        const int64_t* c1p = n_out >= 2 ? (const int64_t*)a.cols[in1.b] : nullptr;
+        // every pointer of the emission is read here, once, before its first group. They come out of the ChainArgs
+        // copy, which hides their address space from the compiler: the SOP build casts them to global memory
+        // (fu_gp), so the loads and stores below are global_* and count against vmcnt only, not against the LDS /
+        // scalar counter as flat_* do. Bases at the block's first row: a lane's offset is its 16-bit row
+        const auto c0p = fu_gp<FIX>(n_out >= 1 ? (const int64_t*)a.cols[in0.b] + lo : nullptr);
+        const auto c1p = fu_gp<FIX>(n_out >= 2 ? (const int64_t*)a.cols[in1.b] + lo : nullptr);
         // emission-only columns in arrival order: read at the rows' original positions (op / oq)
         const int64_t* o0 = OC && n_out >= 1 && ((a.ocol_mask >> in0.b) & 1u) ? (const int64_t*)a.ocols[in0.b] : nullptr;
         const int64_t* o1 = OC && n_out >= 2 && ((a.ocol_mask >> in1.b) & 1u) ? (const int64_t*)a.ocols[in1.b] : nullptr;
-        int64_t* const ov0 = a.out_vals;
-        int64_t* const ov1 = a.out_vals + a.out_cap;
+        const auto origp = fu_gp<FIX>(ONEK ? (const uint32_t*)nullptr : a.orig + lo);
+        const int64_t seq_base = a.seq_base;
+        const auto ots = fu_gp<FIX>(a.out_ts);
+        const auto oes = fu_gp<FIX>(a.out_emit_seq);
+        const auto ofs = fu_gp<FIX>(a.out_first_seq);
+        const auto ov0 = fu_gp<FIX>(a.out_vals);
+        const auto ov1 = fu_gp<FIX>(a.out_vals + a.out_cap);
         // FU_EH rounds at a time: their loads, then their stores. All FU_PT rounds at once needs 24 more VGPRs than
         // the 8-waves-per-SIMD build has (64): it spilled the values to scratch and waited on every load (r3zb)
         constexpr int FU_EH = W >= 8 ? 2 : FU_PT;
 #pragma unroll
-        for (int h = 0; h < FU_PT; h += FU_EH) {
+        for (int h0 = 0; h0 < FU_PT; h0 += FU_EH) {
             uint32_t op[FU_EH], oq[FU_EH];
             int64_t v0[FU_EH], v1[FU_EH];
 #pragma unroll
             for (int i = 0; i < FU_EH; ++i) {
-                const int k = h + i;
+                const int k = h0 + i;
                 if (slot[k] != NOSLOT) {
-                    op[i] = ONEK ? (uint32_t)orig_of(a, lo + prow[k]) : a.orig[lo + prow[k]];
-                    oq[i] = ONEK ? (uint32_t)orig_of(a, lo + qrow[k]) : a.orig[lo + qrow[k]];
-                    if (fast && n_out >= 1) v0[i] = OC && o0 ? o0[in0.a == 0 ? op[i] : oq[i]] : c0p[lo + (in0.a == 0 ? prow[k] : qrow[k])];
-                    if (fast && n_out >= 2) v1[i] = OC && o1 ? o1[in1.a == 0 ? op[i] : oq[i]] : c1p[lo + (in1.a == 0 ? prow[k] : qrow[k])];
+                    op[i] = ONEK ? (uint32_t)orig_of(a, lo + prow[k]) : origp[prow[k]];
+                    oq[i] = ONEK ? (uint32_t)orig_of(a, lo + qrow[k]) : origp[qrow[k]];
+                    if (fast && n_out >= 1) v0[i] = OC && o0 ? o0[e2_0 ? oq[i] : op[i]] : c0p[e2_0 ? qrow[k] : prow[k]];
+                    if (fast && n_out >= 2) v1[i] = OC && o1 ? o1[e2_1 ? oq[i] : op[i]] : c1p[e2_1 ? qrow[k] : prow[k]];
                 }
             }
 #pragma unroll
             for (int i = 0; i < FU_EH; ++i) {
-                const int k = h + i;
+                const int k = h0 + i;
                 if (slot[k] != NOSLOT) {
-                    a.out_ts[slot[k]] = tbase + (int64_t)s_ts[sw(res[k])];
-                    a.out_emit_seq[slot[k]] = a.seq_base + (int64_t)oq[i];
-                    a.out_first_seq[slot[k]] = a.seq_base + (int64_t)op[i];
+                    ots[slot[k]] = tbase + (int64_t)s_ts[sw(res[k])];
+                    oes[slot[k]] = seq_base + (int64_t)oq[i];
+                    ofs[slot[k]] = seq_base + (int64_t)op[i];
                     if (fast && n_out >= 1) ov0[slot[k]] = v0[i];
                     if (fast && n_out >= 2) ov1[slot[k]] = v1[i];
                 }
@@ -1646,7 +1740,7 @@ __global__ __launch_bounds__(FU_THREADS, W) void chain_fused_k(const ChainArgs* 
         const int64_t p = lo + s_row[sw(pos)];
         if (out == MQ_CARRY) {
             const int64_t cs = (int64_t)bbase[1] + wcnt[1][k][w] + __popcll(bc & lt);
-            if (cs >= a.carry_cap) atomicOr(&a.flags[0], 1);
+            if (cs >= a.carry_cap) atomicOr(&h.flags[0], 1);
             else if (FU_OK(p < a.n, 7))
                 emit_carry(a, View{}, cs, p, ((uint32_t)s_lk[sw(pos)] << a.bbits) | (uint32_t)b, a.seq_base + (ONEK ? orig_of(a, p) : (int64_t)a.orig[p]));
         } else {
@@ -2405,6 +2499,35 @@ bool chain_fused_ocols_ok(const ChainArgs& a) {  // the OC instantiation: the sc
     return a.sp.scan_col_kind == a.sp.scan_t && w8 && !a.fu_check_ts;
 }
 
+// the SOP build's by-value arguments, resolved from the flush's ChainArgs (the caller checked the SOP shape: the slim
+// view, the scan's own kind, e1's operand = the scan column)
+static FusedArgs fused_args(const ChainArgs& a) {
+    const ChainSpec& sp = a.sp;
+    FusedArgs f = {};
+    f.xcol = a.cols[sp.scan_col];
+    f.lkey = a.lkey;
+    f.ts32 = a.ts32;
+    f.ts_base = a.ts_base;
+    f.bstart = a.bstart;
+    f.bseg = a.bseg;
+    f.bown = a.bown;
+    f.flags = a.flags;
+    f.dbg = a.dbg;
+    f.n = a.n;
+    f.within_u = sp.has_within ? (uint64_t)sp.within_ms : ~0ull;
+    f.nb = a.nb;
+    f.bbits = a.bbits;
+    f.lbits = a.lbits;
+    f.xcds = a.xcds;
+    f.sub_dead = a.sub_dead;
+    f.fu_skip = a.fu_skip;
+    // the e1 filter: `x OP const` in the scan's own kind, none, or anything else (evaluated from the ChainArgs copy)
+    f.f0_mode = a.f0_on_x && sp.f0.t == sp.scan_t ? FU_F0_TYPED : !a.f0_on_x && sp.f0.kind == FP_TRUE ? FU_F0_TRUE : FU_F0_GEN;
+    f.f0_op = sp.f0.op;
+    f.f0_konst = sp.f0.konst;
+    return f;
+}
+
 void chain_fused(const ChainArgs& a, const ChainArgs* d_a, int64_t grid, hipStream_t stream) {
     if (a.n <= 0) return;
     if (a.ocol_mask && !chain_fused_ocols_ok(a)) throw std::runtime_error("chain_fused: arrival-order columns need the OC build");
@@ -2414,14 +2537,14 @@ void chain_fused(const ChainArgs& a, const ChainArgs* d_a, int64_t grid, hipStre
     const bool w8 = wv ? atoi(wv) == 8 : SDG_FU_W8_DEFAULT;
 #define FU_LAUNCH(KK)                                                                                    \
     do {                                                                                                 \
-        if (a.ocol_mask) hipLaunchKernelGGL((chain_fused_k<KK, true, 8, false, true>), g, b, 0, stream, d_a); \
-        else if (a.fu_check_ts && same) hipLaunchKernelGGL((chain_fused_k<KK, true, 8, true>), g, b, 0, stream, d_a); \
-        else if (a.fu_check_ts) hipLaunchKernelGGL((chain_fused_k<KK, false, 8, true>), g, b, 0, stream, d_a); \
-        else if (same && w8) hipLaunchKernelGGL((chain_fused_k<KK, true, 8>), g, b, 0, stream, d_a);     \
-        else if (same) hipLaunchKernelGGL((chain_fused_k<KK, true, 6>), g, b, 0, stream, d_a);          \
-        else if (w8) hipLaunchKernelGGL((chain_fused_k<KK, false, 8>), g, b, 0, stream, d_a);           \
-        else hipLaunchKernelGGL((chain_fused_k<KK, false, 6>), g, b, 0, stream, d_a);                   \
-    } while (0)
+        if (a.ocol_mask) hipLaunchKernelGGL((chain_fused_k<KK, true, 8, false, true>), g, b, 0, stream, d_a, 0); \
+        else if (a.fu_check_ts && same) hipLaunchKernelGGL((chain_fused_k<KK, true, 8, true>), g, b, 0, stream, d_a, 0); \
+        else if (a.fu_check_ts) hipLaunchKernelGGL((chain_fused_k<KK, false, 8, true>), g, b, 0, stream, d_a, 0); \
+        else if (same && w8) hipLaunchKernelGGL((chain_fused_k<KK, true, 8>), g, b, 0, stream, d_a, 0);     \
+        else if (same) hipLaunchKernelGGL((chain_fused_k<KK, true, 6>), g, b, 0, stream, d_a, 0);          \
+        else if (w8) hipLaunchKernelGGL((chain_fused_k<KK, false, 8>), g, b, 0, stream, d_a, 0);           \
+        else hipLaunchKernelGGL((chain_fused_k<KK, false, 6>), g, b, 0, stream, d_a, 0);                   \
+    } while (0)  /* (the int: these builds' unused FusedArgs slot) */
     // the compile-time operator build (SOP): `e2.x OP e1.x` on the scan column, an ordering OP, the work queue
     const bool e1_is_x = a.sp.scan_mode == SCAN_E1 && a.sp.e1_col == a.sp.scan_col && a.sp.e1_col_kind == a.sp.scan_col_kind;
     const uint8_t op = a.sp.scan_op;
@@ -2431,12 +2554,13 @@ void chain_fused(const ChainArgs& a, const ChainArgs* d_a, int64_t grid, hipStre
         (a.sp.scan_t == VK_F64 || a.sp.scan_t == VK_I64 || a.sp.scan_t == VK_I32 || a.sp.scan_t == VK_F32)) {
         // x beats y: e2 on the left (e2.x OP e1.x) is x OP y, else y OP x = x OP' y (the flipped ordering)
         const uint8_t sop = a.sp.scan_e2_left ? op : op == CMP_GT ? CMP_LT : op == CMP_GE ? CMP_LE : op == CMP_LT ? CMP_GT : CMP_GE;
+        const FusedArgs fa = fused_args(a);
 #define FU_SOP(KK)                                                                                                    \
     do {                                                                                                              \
-        if (sop == CMP_GT) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_GT>), g, b, 0, stream, d_a); \
-        else if (sop == CMP_GE) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_GE>), g, b, 0, stream, d_a); \
-        else if (sop == CMP_LT) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_LT>), g, b, 0, stream, d_a); \
-        else hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_LE>), g, b, 0, stream, d_a);             \
+        if (sop == CMP_GT) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_GT>), g, b, 0, stream, d_a, fa); \
+        else if (sop == CMP_GE) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_GE>), g, b, 0, stream, d_a, fa); \
+        else if (sop == CMP_LT) hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_LT>), g, b, 0, stream, d_a, fa); \
+        else hipLaunchKernelGGL((chain_fused_k<KK, true, SDG_FU_W8, false, false, CMP_LE>), g, b, 0, stream, d_a, fa);             \
     } while (0)
         switch (a.sp.scan_t) {
             case VK_I32: FU_SOP(VK_I32); break;

@@ -251,7 +251,10 @@ constexpr int DQ_DEPTH = 8;                          // deque entries per lane (
 size_t chain_lds_bytes(const ChainArgs& a);
 // deque path: rows -> mq (+ overflow rows resolved by forward scans)
 void chain_deque(const ChainArgs& a, const ChainArgs* d_a, hipStream_t stream);
-// kernel arguments are read from a device copy (d_a) of `a`: the struct is too large to index as a kernarg
+// kernel arguments are read from a device copy (d_a) of `a`. ChainArgs is about 2 KB (the spec's bytecode tables and
+// per-column arrays), within the 4 KB kernel-argument limit, but it is indexed at run time (cols[sp.scan_col]), which
+// a kernarg cannot be without a copy to scratch. The fused matcher's SOP build takes the resolved subset by value
+// instead (FusedArgs below)
 void chain_match(const ChainArgs& a, const ChainArgs* d_a, hipStream_t stream);
 void chain_carry(const ChainArgs& a, const ChainArgs* d_a, hipStream_t stream);
 // sorted-view matcher (radix path): LDS-staged blocks of FU_ROWS sorted rows, chunked deque + forward scans, matches
@@ -287,6 +290,36 @@ constexpr int FU_DQ = SDG_FU_DQ;
 #endif
 constexpr int FU_HALO = SDG_FU_HALO;
 constexpr int FU_OWN = FU_ROWS - FU_HALO;            // candidate rows per block
+// The SOP build's argument block (round 7), passed BY VALUE: what the block start, the staging and the matching read,
+// resolved by the host from the ChainArgs of the flush (chain_fused). Pointers that arrive in the kernel-argument
+// segment are known to be global memory, so those accesses compile to global_* with a scalar base and a 32-bit row
+// offset; read through `const ChainArgs*` every pointer came out of memory and every access was flat_* (counted
+// against both the vector-memory and the LDS / scalar wait counters). Fields that exist in ChainArgs keep its names
+// and meaning. Kernel arguments stay in SGPRs from the kernel's entry to their last use, and the 8-waves-per-SIMD
+// build has none to spare (with the emission's pointers and caps here as well it spilled 44 SGPRs), so the
+// emission, the carries and the rare paths (an e1 filter on another column) still read the ChainArgs copy where they
+// need it -- the emission through pointers cast to the global address space.
+enum FusedF0 : int32_t { FU_F0_GEN = 0, FU_F0_TRUE = 1, FU_F0_TYPED = 2 };
+struct FusedArgs {
+    const void* xcol;                 // cols[sp.scan_col]
+    const uint8_t* lkey;
+    const uint32_t* ts32;
+    const int64_t* ts_base;
+    const uint32_t* bstart;
+    const uint32_t* bseg;
+    const uint32_t* bown;
+    int* flags;
+    volatile int64_t* dbg;
+    int64_t n;
+    uint64_t within_u;                // the window in ms (~0: none)
+    int64_t f0_konst;                 // FU_F0_TYPED: the e1 filter is `x f0_op f0_konst` in the scan's own kind
+    int32_t nb, bbits, lbits, xcds;
+    int32_t sub_dead, fu_skip;
+    int32_t f0_mode;                  // FusedF0 (FU_F0_GEN: evaluated from the ChainArgs copy)
+    int32_t f0_op;
+};
+static_assert(sizeof(FusedArgs) <= 256, "FusedArgs travels in the kernel-argument segment");
+
 // grid size for n rows in nb buckets (a multiple of g_xcds: the XCD remap needs it)
 int64_t chain_fused_grid(int64_t n, int nb, int own = FU_OWN);
 void chain_fused(const ChainArgs& a, const ChainArgs* d_a, int64_t grid, hipStream_t stream);
